@@ -6,8 +6,17 @@ Step = one full RHO join (partition pass 1 + pass 2 + build/probe, count-only) o
 the global relations are N * 2^28 and are radix-sharded with an RCCL all-to-all of
 each relation in pieces, sgxamd.dist).  Inputs are resident in HBM before the timed region.
 
+A plain run (`--gpus N --steps K --warmup W`) generates the relations, runs W untimed and
+K timed steps, writes the last timed step's outputs if `--dump-outputs DIR` is given and
+prints the line: value, ms_per_step, the plan and the match check, nothing measured beside
+them.  `--full` adds every other section described below (per-kernel table and roofline,
+stream ceilings, whole-tuple leg, configs 1 / 4 / 5, scans, reference shapes, TPC-H, CPU
+baselines), each still switched off by its own --no-* option.
+
 One JSON line (rank 0):
   value = probed tuples (|S|, all ranks) per second over the whole join, in millions;
+  ms_per_step = wall milliseconds of one timed step (the timed region / --steps);
+With --full:
   roofline = the dominant kernel's algorithmic bytes / its HIP-event time vs 8 TB/s;
   cpu_baseline = the oracle's restated reference RHO (oracle/rho_oracle.c, pthreads)
   on a bounded sample of reference-generated relations on this host's cores.
@@ -349,6 +358,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also measure the per-kernel table and roofline, the stream "
+                         "ceilings, the whole-tuple leg, configs 1 / 4 / 5, the scans, the reference's shapes, "
+                         "TPC-H and the CPU baselines (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float64; rank 0): "
+                         "matches.npy, the join's global match count, shape (1,)")
     ap.add_argument("--log2n", type=int, default=28, help="c2: per-GPU |R| = |S| = 2^log2n")
     ap.add_argument("--workload", choices=["c2", "c4", "c5"], default="c2",
                     help="BASELINE config: c2 = pk/fk 2^28 per GPU (weak), c4 = |R| 2^27 x |S| 2^30 "
@@ -375,6 +391,8 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="time budget per CPU baseline leg")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         rc = spawn_ranks(args, sys.argv[1:])
@@ -476,8 +494,10 @@ def main():
         torch.cuda.synchronize()
         return R, S, gR, gS, desc, gen
 
-    def measure_rho(workload: str, R, S, gR: int, gS: int):
-        """W untimed + K timed steps of the (sharded) join; max over ranks."""
+    def measure_rho(workload: str, R, S, gR: int, gS: int, table: bool = True):
+        """W untimed + K timed steps of the (sharded) join; max over ranks.  `table`: the
+        full-timing pass after the timed region (a plain run has only the timed region's
+        own two spans in per_kernel)."""
         N_glob = gS  # every S tuple matches exactly one R tuple in all three configs
 
         def step():
@@ -506,7 +526,7 @@ def main():
         if not ok:
             raise SystemExit(f"{workload}: wrong match count {[r.matches for r in results]} != {N_glob}")
         per_kernel: dict[str, list[float]] = {}
-        for _ in range(TABLE_STEPS):
+        for _ in range(TABLE_STEPS if table else 0):
             r_t = step()
             if r_t.matches != N_glob:
                 raise SystemExit(f"{workload}: wrong match count {r_t.matches} != {N_glob}")
@@ -555,10 +575,61 @@ def main():
     sgxamd.set_partition_overlap(bool(args.partition_overlap))
     R, S, gR, gS, workload, gen_desc = make_relations(args.workload)
     N_glob = gS
-    results, per_kernel, elapsed = measure_rho(args.workload, R, S, gR, gS)
+    results, per_kernel, elapsed = measure_rho(args.workload, R, S, gR, gS, table=args.full)
     ok = True
     value = N_glob * args.steps / elapsed / 1e6  # M probed tuples/s, all ranks
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        # what the step's caller receives from the last timed step: a counting join returns its count
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "matches.npy"), np.array([results[-1].matches], dtype=np.float64))
+    ls = results[-1].local_stats
+    # the join's own record of the last timed step (nothing measured beside the timed region)
+    rho_head = {
+        "matches_ok": ok, "matches": results[-1].matches, "generator": gen_desc,
+        "M_rec_per_s_reference_formula": round((gR + gS) * args.steps / elapsed / 1e6, 1),
+        "partition_overlap": bool(args.partition_overlap),
+        "radix_bits": ls.get("radix_bits"), "passes": ls.get("passes"),
+        "partition_layout": LAYOUTS.get(ls.get("layout"), "unknown"),
+        "narrow_partitions": {"R": bool((ls.get("narrow") or 0) & 1), "S": bool((ls.get("narrow") or 0) & 2),
+                              "what": "final partitions hold 2-byte key residuals (key >> radix bits): every "
+                                      "key's residual fits 16 bits (pass 1's largest key)"},
+        "step_ms_breakdown": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in results[-1].ms.items()},
+    }
+
+    def print_line(rho_block: dict, multi: dict | None, **sections):
+        """The result line (rank 0): the headline fields, `rho_block`, then `sections`."""
+        if rank != 0:
+            return
+        line = {
+            "metric": METRIC, "value": round(value, 1), "unit": "M probed tuples/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True, "scaling": "weak" if args.workload == "c2" else "strong",
+            "vs_baseline": None, "dtype": "u32",
+            "data": "synthetic: device-generated pk (shuffled 1..|R|) and "
+                    + ("Zipf(0.75) over 1..|R|" if args.workload == "c5" else "fk (shuffled copies of 1..|R|)")
+                    + " relations, 8-byte {key, payload} tuples",
+            "config": {"workload": workload, "algorithm": args.algorithm, "global_R": gR, "global_S": gS,
+                       "parallelism": f"radix-shard{world}",
+                       "partition_layout": rho_block["partition_layout"],
+                       **({"exchange": results[-1].ms.get("impl", "torch.distributed all_to_all_single (sgxamd.dist)")}
+                          if world > 1 else {}),
+                       **({"dist_backend": "gloo (single-GPU rehearsal, not a scaling number)"}
+                          if world > 1 and args.dist_backend == "gloo" else {})},
+            "full": bool(args.full), **sections, "rho": rho_block,
+        }
+        if multi is not None:
+            line["multi"] = multi
+        print(json.dumps(line), flush=True)
+
+    if not args.full:
+        # the sections of --full are null, as a section switched off by its --no-* option is
+        print_line(rho_head, gather_multi(results[-1]), roofline=None, cpu_baseline=None, scan=None, tpch=None,
+                   reference_shapes=None, configs=None)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     kernel_times = (f"R_pass1_scatter and join_build_probe: HIP events inside the timed region (sparse timing, "
                     f"4 events per step); the other kernels: a full-timing pass of {TABLE_STEPS} steps after it")
     if args.partition_overlap:
@@ -599,7 +670,6 @@ def main():
                 "avg_ms": round(avg[dom], 4), "algorithmic_bytes": algorithmic_bytes(dom, nR, nS, *plan)}
     probe_gbs = algorithmic_bytes("join_build_probe", nR, nS, *plan) / (avg["join_build_probe"] * 1e-3) / 1e9
     phase = {k: round(v, 4) for k, v in sorted(avg.items())}
-    ls = results[-1].local_stats
     # the north-star probe phase and the whole step as scalars of `roofline` (the block
     # the driver's record keeps): the build/probe launch priced at the bytes it reads,
     # and every kernel of one join at its algorithmic bytes over the measured step time
@@ -615,8 +685,7 @@ def main():
         "step_frac": round(step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
     })
     rho_info = {
-        "matches_ok": ok, "matches": results[-1].matches, "generator": gen_desc,
-        "M_rec_per_s_reference_formula": round((gR + gS) * args.steps / elapsed / 1e6, 1),
+        **rho_head, "matches_ok": ok,  # (the isolation pass of --partition-overlap 1 checked its counts too)
         "probe_phase_M_probed_tuples_per_s": round(nS / (avg["join_build_probe"] * 1e-3) / 1e6, 1),
         "probe_roofline": {"achieved": round(probe_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                            "frac": round(probe_gbs / HBM_PEAK_GBS, 4),
@@ -626,13 +695,6 @@ def main():
                                          "(8 B per tuple of R and S) is priced on the whole-tuple leg, "
                                          "rho.tuple_layout.probe_roofline")},
         "kernel_ms_avg": phase, "kernel_times_from": kernel_times,
-        "partition_overlap": bool(args.partition_overlap),
-        "radix_bits": ls.get("radix_bits"), "passes": ls.get("passes"),
-        "partition_layout": LAYOUTS.get(ls.get("layout"), "unknown"),
-        "narrow_partitions": {"R": bool((ls.get("narrow") or 0) & 1), "S": bool((ls.get("narrow") or 0) & 2),
-                              "what": "final partitions hold 2-byte key residuals (key >> radix bits): every "
-                                      "key's residual fits 16 bits (pass 1's largest key)"},
-        "step_ms_breakdown": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in results[-1].ms.items()},
     }
     if args.workload == "c5":
         rho_info["load_report"] = load_report(results[-1], nS)
@@ -1131,28 +1193,8 @@ def main():
                 scan_info["cpu_baseline"] = scan_cpu
             del scan_col_host
 
-    if rank == 0:
-        line = {
-            "metric": METRIC, "value": round(value, 1), "unit": "M probed tuples/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True, "scaling": "weak" if args.workload == "c2" else "strong",
-            "vs_baseline": None, "dtype": "u32",
-            "data": "synthetic: device-generated pk (shuffled 1..|R|) and "
-                    + ("Zipf(0.75) over 1..|R|" if args.workload == "c5" else "fk (shuffled copies of 1..|R|)")
-                    + " relations, 8-byte {key, payload} tuples",
-            "config": {"workload": workload, "algorithm": args.algorithm, "global_R": gR, "global_S": gS,
-                       "parallelism": f"radix-shard{world}",
-                       "partition_layout": rho_info["partition_layout"],
-                       **({"exchange": results[-1].ms.get("impl", "torch.distributed all_to_all_single (sgxamd.dist)")}
-                          if world > 1 else {}),
-                       **({"dist_backend": "gloo (single-GPU rehearsal, not a scaling number)"}
-                          if world > 1 and args.dist_backend == "gloo" else {})},
-            "roofline": roofline, "cpu_baseline": cpu, "rho": rho_info, "scan": scan_info, "tpch": tpch_info,
-            "reference_shapes": paper_info, "configs": configs_info,
-        }
-        if multi_info is not None:
-            line["multi"] = multi_info
-        print(json.dumps(line), flush=True)
+    print_line(rho_info, multi_info, roofline=roofline, cpu_baseline=cpu, scan=scan_info, tpch=tpch_info,
+               reference_shapes=paper_info, configs=configs_info)
     if world > 1:
         dist.destroy_process_group()
 

@@ -18,7 +18,7 @@ for rep in $(seq 1 "$REPS"); do
     ENVARGS=()
     IFS=',' read -ra KV <<< "$envs"
     for kv in "${KV[@]}"; do [ -n "$kv" ] && ENVARGS+=("$kv"); done
-    env "${ENVARGS[@]}" timeout -k 10 300 python bench.py --no-scan --no-tpch --no-cpu-baseline --no-paper --no-configs "$@" \
+    env "${ENVARGS[@]}" timeout -k 10 300 python bench.py --full --no-scan --no-tpch --no-cpu-baseline --no-paper --no-configs "$@" \
       > "$OUT/bench_${label}_$rep.json" 2> "$OUT/bench_${label}_$rep.err" \
       || { echo "bench $label failed"; tail -20 "$OUT/bench_${label}_$rep.err"; exit 1; }
     python3 - "$OUT/bench_${label}_$rep.json" "$label" "$rep" <<'EOF'

@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 for rep in 1 2; do
   for v in $NAMES; do
     if [ "$v" = base ]; then LP=""; else LP="$PWD/varlib/$v/libsgxamd.so"; fi
-    SGXAMD_LIB_PATH=$LP timeout -k 10 300 python bench.py --no-scan --no-tpch --no-cpu-baseline --no-paper --no-configs "$@" \
+    SGXAMD_LIB_PATH=$LP timeout -k 10 300 python bench.py --full --no-scan --no-tpch --no-cpu-baseline --no-paper --no-configs "$@" \
       > "$OUT/bench_${v}_$rep.json" 2> "$OUT/bench_${v}_$rep.err" || { echo "bench $v failed"; tail -20 "$OUT/bench_${v}_$rep.err"; exit 1; }
     python3 -c "
 import json; b=json.load(open('$OUT/bench_${v}_$rep.json')); k=b['rho']['kernel_ms_avg']

@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 for v in $NAMES; do
   if [ "$v" = base ]; then LP=""; else LP="$PWD/varlib/$v/libsgxamd.so"; fi
   SGXAMD_LIB_PATH=$LP timeout -s KILL 180 rocprofv3 --pmc WRITE_SIZE -T -d "$OUT/w_$v" -o w --output-format csv \
-    -- python3 bench.py --steps 2 --warmup 1 --no-scan --no-tpch --no-cpu-baseline --no-paper --no-configs \
+    -- python3 bench.py --full --steps 2 --warmup 1 --no-scan --no-tpch --no-cpu-baseline --no-paper --no-configs \
     --no-tuple-layout > "$OUT/w_$v.log" 2>&1 || { echo "pmc $v failed"; tail -20 "$OUT/w_$v.log"; exit 1; }
   python3 - "$OUT/w_$v" "$KERNEL" "$v" <<'EOF'
 import csv, glob, sys

@@ -13,6 +13,6 @@ if [ $# -gt 0 ]; then
     > "$OUT/gpu_tests.log" 2>&1 || { echo "tests failed"; grep -E "FAILED|ERROR|Error|assert" "$OUT/gpu_tests.log" | tail -30; exit 1; }
   grep -E "passed|failed" "$OUT/gpu_tests.log" | tail -3
 fi
-timeout -k 10 900 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" \
+timeout -k 10 900 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" \
   || { echo "bench failed"; tail -30 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"

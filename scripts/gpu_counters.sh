@@ -14,7 +14,7 @@ for grp in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ
            "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_BUSY_CYCLES"; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc $grp -d "$OUT/sq$i" -o sq$i --output-format csv \
-    -- python3 bench.py --steps 2 --warmup 1 --no-scan --no-tpch --no-paper --no-configs --no-tuple-layout \
+    -- python3 bench.py --full --steps 2 --warmup 1 --no-scan --no-tpch --no-paper --no-configs --no-tuple-layout \
        --no-cpu-baseline "$@" > "$OUT/sq$i.log" 2>&1 \
     || { echo "pmc pass $i failed"; tail -20 "$OUT/sq$i.log"; exit 1; }
 done

@@ -11,9 +11,9 @@ timeout -k 10 300 python -u -m pytest -x -v --timeout 120 --timeout-method threa
   || { echo "tests failed"; tail -40 "$OUT/tests.log"; exit 1; }
 tail -3 "$OUT/tests.log"
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29533 bench.py --gpus 2 --steps 3 --warmup 1 --log2n 26 --dist-backend gloo \
+  --master-port 29533 bench.py --full --gpus 2 --steps 3 --warmup 1 --log2n 26 --dist-backend gloo \
   > "$OUT/bench2.json" 2> "$OUT/bench2.err" || { echo "bench2 failed"; tail -30 "$OUT/bench2.err"; exit 1; }
 cat "$OUT/bench2.json"
-timeout -k 10 300 python bench.py --steps 10 --warmup 3 --no-tpch --no-cpu-baseline > "$OUT/bench1.json" 2> "$OUT/bench1.err" \
+timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --no-tpch --no-cpu-baseline > "$OUT/bench1.json" 2> "$OUT/bench1.err" \
   || { echo "bench1 failed"; tail -30 "$OUT/bench1.err"; exit 1; }
 cat "$OUT/bench1.json"

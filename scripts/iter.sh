@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 timeout -k 10 600 python -m pytest tests -m gpu -x -q -p no:cacheprovider > "$OUT/gpu_tests.log" 2>&1 \
   || { echo "gpu tests failed"; tail -40 "$OUT/gpu_tests.log"; exit 1; }
 tail -2 "$OUT/gpu_tests.log"
-timeout -k 10 600 python bench.py --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" \
+timeout -k 10 600 python bench.py --full --no-cpu-baseline "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" \
   || { echo "bench failed"; tail -30 "$OUT/bench.err"; exit 1; }
 python3 - "$OUT/bench.json" <<'PY'
 import json,sys

@@ -75,6 +75,42 @@ def test_bench_refuses_world_mismatch():
     assert "refusing to measure" in out.stderr
 
 
+def test_bench_refuses_zero_steps():
+    """ms_per_step is the timed region over --steps: no steps, no line."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True,
+                         text=True, timeout=60)
+    assert out.returncode == 2 and out.stdout.strip() == ""
+
+
+@pytest.mark.gpu
+def test_plain_run_line_and_dump(gpu, tmp_path):
+    """A plain run (no --full) at a small size: the line carries the headline fields and
+    null sections, --steps is the number of timed steps, and --dump-outputs writes the
+    last step's match count (|S|: every fk tuple matches one pk tuple) as float64."""
+    import numpy as np
+
+    log2n = 20
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--log2n", str(log2n), "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=110)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = out.stdout.strip().splitlines()
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["full"] is False
+    assert d["unit"] == "M probed tuples/s" and d["higher_is_better"] is True and d["dtype"] == "u32"
+    assert d["ms_per_step"] > 0
+    # value = |S| / step time; the line rounds ms_per_step to 1e-4 ms and value to 0.1
+    rounding = d["value"] * 0.5e-4 / (d["ms_per_step"] - 0.5e-4) + 0.05
+    assert abs(d["value"] - (1 << log2n) / (d["ms_per_step"] * 1e-3) / 1e6) <= 1.01 * rounding
+    assert d["rho"]["matches_ok"] and d["rho"]["matches"] == 1 << log2n
+    for section in ("roofline", "cpu_baseline", "scan", "tpch", "reference_shapes", "configs"):
+        assert d[section] is None
+    assert sorted(p.name for p in (tmp_path / "dump").iterdir()) == ["matches.npy"]
+    m = np.load(tmp_path / "dump" / "matches.npy")
+    assert m.dtype == np.float64 and m.tolist() == [float(1 << log2n)]
+
+
 @pytest.mark.parametrize("kernel,expect", [("R_pass1_scatter", 13), ("S_pass2_scatter", 8), ("join_build_probe", 4)])
 def test_algorithmic_bytes_keys_layout(kernel, expect):
     """Bytes per tuple the roofline prices (keys layout, 7-bit pass-2 digit)."""
