@@ -7,6 +7,17 @@
 //       radix_join.h (RHT, implemented at radix_join.cpp:1645-1648)    (_Z3RHTPK7table_tS1_PK12joinconfig_t)
 //   void run_join(result_t*, const table_t*, const table_t*, const char*, const joinconfig_t*)
 //       Join-Benchmarks/lib/Joins/include/joins.hpp / src/joins.cpp:55-78
+//   result_t *PHT / PHT_no_overflow / PHT_unrolled / PHT_overflow(const table_t*, const table_t*, const joinconfig_t*)
+//       Join-Benchmarks/lib/Joins/include/npj/no_partitioning_hash_join.hpp:6-16
+//       (_Z3PHTPK7table_tS1_PK12joinconfig_t, _Z15PHT_no_overflowPK7table_tS1_PK12joinconfig_t,
+//        _Z12PHT_unrolledPK7table_tS1_PK12joinconfig_t, _Z12PHT_overflowPK7table_tS1_PK12joinconfig_t)
+//       All four run the one no-partitioning GPU join (mi355_npo_join): the count is exact
+//       for any input, also where the reference's no-overflow variants write past a full
+//       bucket.  They print the npj print_timing lines (HashLinkTableCommon.cpp:13-29).
+//       run_join also knows the table names NPO_st and NPO_no (joins.cpp:38-39), but no
+//       C++ symbol is exported for them: the reference's header declares NPO_st / NPO_no
+//       while its table names NPO_single_thread / NPO_no_overflow, so no consistent
+//       symbol exists to match.
 // so an unmodified run_join-style caller (App/TEEBench/native.cpp:137, the TPC-H
 // queries) links against libsgxamd.so instead of the CPU join library.
 // With config->MATERIALIZE = 1 the result carries the reference's chunked_table_t
@@ -20,6 +31,10 @@
 
 result_t *RHO(const table_t *relR, const table_t *relS, const joinconfig_t *config);
 result_t *RHT(const table_t *relR, const table_t *relS, const joinconfig_t *config);
+result_t *PHT(const table_t *relR, const table_t *relS, const joinconfig_t *config);
+result_t *PHT_no_overflow(const table_t *relR, const table_t *relS, const joinconfig_t *config);
+result_t *PHT_unrolled(const table_t *relR, const table_t *relS, const joinconfig_t *config);
+result_t *PHT_overflow(const table_t *relR, const table_t *relS, const joinconfig_t *config);
 
 void run_join(result_t *res, const table_t *relR, const table_t *relS, const char *algorithm_name,
               const joinconfig_t *config);

@@ -193,6 +193,57 @@ void mi355_set_stream(void *stream);
  * process.  MI355_ERR_INVALID while a pipelined join is pending. */
 int mi355_release_workspace(void);
 
+/*
+ * No-partitioning hash join: the reference's PHT family (PHT, PHT_no_overflow,
+ * PHT_unrolled, PHT_overflow: npj/no_partitioning_hash_join.hpp:6-16, table names PHT,
+ * PHT_no, PHT_un, PHT_o, NPO_st, NPO_no at joins.cpp:34-39).  One global hash table
+ * (bucket = key & (num_buckets - 1), two slots per bucket, overflow chains) is built
+ * over all of R in HBM and every S tuple probes it.  The count is exact for any input:
+ * where the reference's no-overflow variants write past a full bucket, this join
+ * chains.  No multi-GPU form, no key_shift, no begin/finish pipeline.
+ */
+#define MI355_ALGO_PHT 2 /* name only; mi355_rho_opts.algorithm does not accept it */
+
+typedef struct mi355_npo_opts {
+    int bucket_bits;  /* log2 of the bucket count (1..31); 0 = the reference's next_pow2(nR / 2) */
+    int materialize;  /* 1 = write every match to out, as mi355_rho_opts.materialize */
+    int timing;       /* 1 = record the clear, build and probe launches (mi355_timing_get) */
+    void *stream;     /* hipStream_t to launch on; NULL = the library's stream */
+    struct output_triple_t *out; /* host or device memory; order unspecified */
+    uint64_t out_capacity;       /* triples that fit in out; if fewer than the matches, the call
+                                    returns MI355_ERR_CAPACITY with stats->matches = required */
+} mi355_npo_opts;
+
+typedef struct mi355_npo_stats {
+    uint64_t matches;        /* join cardinality */
+    uint64_t num_buckets;
+    uint64_t overflow_nodes; /* R tuples beyond two in their bucket */
+    uint64_t max_chain;      /* longest overflow chain: not free to compute, always 0 */
+    uint64_t table_bytes;    /* buckets (+ slot payloads, + the nodes in use) */
+    double ms_h2d;           /* host->device staging (0 when inputs were resident) */
+    double ms_clear;         /* the table clear runs inside the timed span (the reference's
+                                memset is outside its timer); 0, as ms_build and ms_probe,
+                                when timing is off: then only ms_total is measured */
+    double ms_build;
+    double ms_probe;         /* count probe (+ the materialising probe) */
+    double ms_total;         /* clear + build + probe, device time */
+} mi355_npo_stats;
+
+/* Drop-in for PHT() and its variants: same result contract as mi355_rho_join. */
+int mi355_npo_join(const struct table_t *R, const struct table_t *S, const struct joinconfig_t *cfg,
+                   struct result_t *out);
+
+/* The join on raw tuple arrays (host or device, up to 2^31 tuples each).  nR == 0 or
+ * nS == 0: MI355_OK, 0 matches, no launch.  A table or node pool that cannot be
+ * allocated: MI355_ERR_OOM. */
+int mi355_npo_join_ex(const struct row_t *R, uint64_t nR, const struct row_t *S, uint64_t nS,
+                      const mi355_npo_opts *opts, mi355_npo_stats *stats);
+
+/* Statistics of the last no-partitioning join on this thread.  mi355_last_join_stats
+ * reports its matches, ms_build, ms_probe, ms_join (= clear + build + probe) and ms_total,
+ * the radix fields 0. */
+int mi355_last_npo_stats(mi355_npo_stats *out);
+
 /* HBM ceiling probe (measurement: bench.py's roofline ceilings).  One grid-stride
  * streaming kernel of 256-thread workgroups over device buffers, enqueued on `stream`
  * (null: the library stream): kind 0 copies `bytes` from src to dst, 1 reads src (dst:

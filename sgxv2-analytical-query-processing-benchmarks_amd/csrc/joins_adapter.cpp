@@ -3,6 +3,8 @@
 // RHO / RHT: radix_join.cpp:1640-1648 -> mi355_rho_join / mi355_rht_join, plus the reference's
 //      print_timing log lines (radix_join.cpp:252-293) so that
 //      SGXv2Scripts/scripts/helpers/runner.py:14-55 parses our output unchanged.
+// PHT / PHT_no_overflow / PHT_unrolled / PHT_overflow: no_partitioning_hash_join.cpp:166-249 ->
+//      mi355_npo_join, plus the npj print_timing lines (HashLinkTableCommon.cpp:13-29).
 // run_join: joins.cpp:55-78 (strcmp lookup in an algorithm table, memcpy of the
 //      result; like the reference, the callee's result_t is not freed).
 #include <algorithm>
@@ -52,9 +54,19 @@ int rho_entry(const table_t *relR, const table_t *relS, const joinconfig_t *conf
     return mi355_rho_join(relR, relS, config, out);
 }
 
-const algorithm_t mi355_algorithms[] = {  // joins.cpp:33-53, the radix joins this library replaces
+// NPO_st / NPO_no have no C++ symbol (sgxamd/joins.hpp): their table entries call this
+result_t *npo_by_name(const table_t *relR, const table_t *relS, const joinconfig_t *config);
+
+const algorithm_t mi355_algorithms[] = {  // joins.cpp:33-53, the joins this library replaces
     {"RHO", RHO},
     {"RHT", RHT},
+    // the no-partitioning family (joins.cpp:34-39): one GPU join behind every name
+    {"PHT", PHT},
+    {"PHT_no", PHT_no_overflow},
+    {"PHT_un", PHT_unrolled},
+    {"PHT_o", PHT_overflow},
+    {"NPO_st", npo_by_name},
+    {"NPO_no", npo_by_name},
     {"", nullptr},
 };
 
@@ -120,7 +132,62 @@ result_t *radix_dropin(const char *name, const table_t *relR, const table_t *rel
     return res;
 }
 
+// PHT and its variants: mi355_npo_join, then the npj print_timing lines
+// (HashLinkTableCommon.cpp:13-29) in the reference's order and format.
+result_t *npo_dropin(const char *name, const table_t *relR, const table_t *relS, const joinconfig_t *config) {
+    LOG_INFO("Running %s on MI355X (%s)", name, mi355_version());
+    const auto t_start = std::chrono::steady_clock::now();
+    auto *res = static_cast<result_t *>(std::malloc(sizeof(result_t)));
+    const int rc = mi355_npo_join(relR, relS, config, res);
+    const auto t_end = std::chrono::steady_clock::now();
+    if (rc != MI355_OK) {
+        LOG_ERROR("%s failed (%d): %s", name, rc, mi355_last_error());
+        std::exit(EXIT_FAILURE);
+    }
+    mi355_npo_stats st{};
+    mi355_last_npo_stats(&st);
+    const uint64_t num = relR->num_tuples + relS->num_tuples;
+    const double wall_us = std::chrono::duration<double, std::micro>(t_end - t_start).count();
+    const uint64_t C = cpms();
+    auto cyc = [&](double ms) { return static_cast<unsigned long>(ms * 1000.0 * C); };
+    const unsigned long total = cyc(st.ms_total);
+    const unsigned long usec_tsc = total / C;
+    LOG_INFO("Hash table: %lu buckets, %lu overflow nodes, %lu bytes; clear (cycles) %lu, inside the total",
+             (unsigned long)st.num_buckets, (unsigned long)st.overflow_nodes, (unsigned long)st.table_bytes,
+             cyc(st.ms_clear));
+    LOG_INFO("Total input tuples : %lu", (unsigned long)num);
+    LOG_INFO("Result tuples : %lu", (unsigned long)st.matches);
+    LOG_INFO("Total Join Time (cycles)    : %lu", total);
+    LOG_INFO("Build (cycles)              : %lu", cyc(st.ms_build));
+    LOG_INFO("Join (cycles)               : %lu", cyc(st.ms_probe));
+    LOG_INFO("Cycles-per-tuple : %.4lf", (double)total / (num ? (double)num : 1.0));
+    LOG_INFO("Total Runtime (us) : %lu ", (unsigned long)wall_us);
+    LOG_INFO("Total RT from TSC (us) : %lu ", usec_tsc);
+    LOG_INFO("Throughput (M rec/sec) : %.2lf", usec_tsc ? (double)num / (double)usec_tsc : 0.0);
+    return res;
+}
+
+result_t *npo_by_name(const table_t *relR, const table_t *relS, const joinconfig_t *config) {
+    return npo_dropin("NPO", relR, relS, config);
+}
+
 }  // namespace
+
+result_t *PHT(const table_t *relR, const table_t *relS, const joinconfig_t *config) {
+    return npo_dropin("PHT", relR, relS, config);
+}
+
+result_t *PHT_no_overflow(const table_t *relR, const table_t *relS, const joinconfig_t *config) {
+    return npo_dropin("PHT_no_overflow", relR, relS, config);
+}
+
+result_t *PHT_unrolled(const table_t *relR, const table_t *relS, const joinconfig_t *config) {
+    return npo_dropin("PHT_unrolled", relR, relS, config);
+}
+
+result_t *PHT_overflow(const table_t *relR, const table_t *relS, const joinconfig_t *config) {
+    return npo_dropin("PHT_overflow", relR, relS, config);
+}
 
 result_t *RHO(const table_t *relR, const table_t *relS, const joinconfig_t *config) {
     return radix_dropin("RHO", relR, relS, config, rho_entry);

@@ -85,7 +85,10 @@ void Timer::begin_call(hipStream_t s, bool enabled, bool coarse) {
 // -- R's pass-1 scatter and the build/probe -- and one "other" span between them, so a
 // timed step carries 4 events instead of one per kernel (each event between two kernels
 // costs 4.5-4.8 us of GPU time even without the system fence: r06q kernel trace).
-static bool sparse_kept(const std::string &n) { return n == "R_pass1_scatter" || n == "join_build_probe"; }
+// The no-partitioning join's three spans (npo_*) are all kept.
+static bool sparse_kept(const std::string &n) {
+    return n == "R_pass1_scatter" || n == "join_build_probe" || n.compare(0, 4, "npo_") == 0;
+}
 
 void Timer::mark(const char *name) {
     if (!enabled_ || (coarse_ && open_ev_)) return;
@@ -192,7 +195,8 @@ void release_workspace(Context *ctx) {
     for (DeviceBuffer *b : {&ctx->inR, &ctx->inS, &ctx->t1R, &ctx->t1S, &ctx->t2R, &ctx->t2S, &ctx->sideR, &ctx->sideS,
                             &ctx->scratch.buf, &ctx->mat, &ctx->tp_mask, &ctx->tp_blk, &ctx->tp_trip, &ctx->scan_in,
                             &ctx->scan_out, &ctx->scan_aux, &ctx->scan_dict, &ctx->xsendR, &ctx->xsendS, &ctx->xrecvR,
-                            &ctx->xrecvS, &ctx->wsendR, &ctx->wsendS, &ctx->wrecvR, &ctx->wrecvS, &ctx->wscratch.buf})
+                            &ctx->xrecvS, &ctx->wsendR, &ctx->wsendS, &ctx->wrecvR, &ctx->wrecvS, &ctx->wscratch.buf, &ctx->npo_table, &ctx->npo_bpay, &ctx->npo_nodes,
+                            &ctx->npo_npay})
         b->release();
     for (DeviceBuffer &b : ctx->tp_cols) b.release();
     for (DeviceBuffer &b : ctx->tp_rel) b.release();

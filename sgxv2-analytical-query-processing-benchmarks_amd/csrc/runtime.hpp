@@ -84,6 +84,10 @@ struct Context {
     DeviceBuffer sideR, sideS;     // pass-2 digit per pass-1 output tuple (two-pass plans)
     Arena scratch;
     DeviceBuffer mat;              // materialised output_triple_t (when the caller's buffer is host memory)
+    // no-partitioning join (npo_host.cpp): control words + buckets, the slots' payloads,
+    // the overflow nodes and their payloads (the pool: allocated by the first join that
+    // overflows a bucket)
+    DeviceBuffer npo_table, npo_bpay, npo_nodes, npo_npay;
     // TPC-H workspace: staged host columns, selection bits/offsets, intermediate
     // relations and join-result triples
     DeviceBuffer tp_cols[12], tp_mask, tp_blk, tp_rel[3], tp_trip;

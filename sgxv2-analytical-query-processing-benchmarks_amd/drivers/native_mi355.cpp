@@ -1,5 +1,5 @@
 // native_mi355 — the reference's native join driver (Join-Benchmarks/App/TEEBench/native.cpp)
-// running RHO or RHT (-a) on an MI355X through run_join() of libsgxamd.so; -m materialises
+// running RHO, RHT or the PHT family (-a) on an MI355X through run_join() of libsgxamd.so; -m materialises
 // the result into the reference's chunked table (CHUNKED_TABLE build).
 //
 // Same CLI (commons.cpp:10-190 getopt "a:c:d:e:l:n:mr:s:t:u:x:y:z:hv"), the same
@@ -47,7 +47,7 @@ int main(int argc, char **argv) {
             case 'x': r_size = std::strtoull(optarg, nullptr, 10) * 1024 * 1024 / 8; break;
             case 'y': s_size = std::strtoull(optarg, nullptr, 10) * 1024 * 1024 / 8; break;
             case 'z': skew = std::atof(optarg); break;
-            case 'h': std::printf("native_mi355 -a RHO|RHT -r N -s N [-l sel] [-z theta] [-n threads] [-m]\n"); return 0;
+            case 'h': std::printf("native_mi355 -a RHO|RHT|PHT|PHT_no|PHT_un|PHT_o|NPO_st|NPO_no -r N -s N [-l sel] [-z theta] [-n threads] [-m]\n"); return 0;
             default: break;
         }
     }

@@ -1,4 +1,4 @@
-"""ctypes binding of libsgxamd.so, the MI355X RHO join + predicate scan C-ABI.
+"""ctypes binding of libsgxamd.so, the MI355X RHO / PHT join + predicate scan C-ABI.
 
 This is the Python side of the drop-in boundary declared in include/sgxamd/*.h:
 the same entry points a cgo / JNI / ctypes caller of the reference would bind
@@ -125,6 +125,35 @@ class rho_stats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class npo_opts(C.Structure):  # mi355_npo_opts
+    _fields_ = [
+        ("bucket_bits", C.c_int),
+        ("materialize", C.c_int),
+        ("timing", C.c_int),
+        ("stream", C.c_void_p),
+        ("out", C.c_void_p),
+        ("out_capacity", C.c_uint64),
+    ]
+
+
+class npo_stats(C.Structure):  # mi355_npo_stats
+    _fields_ = [
+        ("matches", C.c_uint64),
+        ("num_buckets", C.c_uint64),
+        ("overflow_nodes", C.c_uint64),
+        ("max_chain", C.c_uint64),
+        ("table_bytes", C.c_uint64),
+        ("ms_h2d", C.c_double),
+        ("ms_clear", C.c_double),
+        ("ms_build", C.c_double),
+        ("ms_probe", C.c_double),
+        ("ms_total", C.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class multi_stats(C.Structure):  # sgxamd/multi.h
     _fields_ = [
         ("matches", C.c_uint64),
@@ -218,6 +247,9 @@ SIGNATURES = {
     "mi355_timing_get": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.c_int]),
     "mi355_set_stream": (None, [_P]),
     "mi355_stream_probe": (C.c_int, [C.c_int, _P, _P, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint32, _P]),
+    "mi355_npo_join": (C.c_int, [C.POINTER(table_t), C.POINTER(table_t), C.POINTER(joinconfig_t), C.POINTER(result_t)]),
+    "mi355_npo_join_ex": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, C.POINTER(npo_opts), C.POINTER(npo_stats)]),
+    "mi355_last_npo_stats": (C.c_int, [C.POINTER(npo_stats)]),
     # multi.h
     "mi355_rho_join_multi_ex": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, C.c_int, C.c_int, C.POINTER(rho_opts),
                                           C.POINTER(multi_stats)]),
@@ -399,6 +431,29 @@ def rho_join(R, nR: int, S, nS: int, *, radix_bits: int = 0, passes: int = 0, ke
     return JoinResult(int(st.matches), st)
 
 
+def npo_join(R, nR: int, S, nS: int, *, bucket_bits: int = 0, timing: bool = False, stream: int | None = None,
+             out=None, out_capacity: int = 0) -> JoinResult:
+    """No-partitioning hash join (the reference's PHT family) of nR R-tuples and nS
+    S-tuples (host or device): one hash table over all of R, probed by every S tuple.
+
+    bucket_bits: log2 of the bucket count (0: next_pow2(nR / 2), as the reference).  `out`
+    and out_capacity as rho_join; stats is the dict of mi355_npo_stats."""
+    o = npo_opts(bucket_bits, 1 if out is not None else 0, 1 if timing else 0, stream or None,
+                 ptr(out) if out is not None else None, out_capacity)
+    st = npo_stats()
+    rc = lib.mi355_npo_join_ex(ptr(R), nR, ptr(S), nS, C.byref(o), C.byref(st))
+    if rc == -5:
+        raise Mi355Error(rc, f"capacity: {int(st.matches)} triples needed")
+    _check(rc)
+    return JoinResult(int(st.matches), st)
+
+
+def last_npo_stats() -> dict:
+    st = npo_stats()
+    _check(lib.mi355_last_npo_stats(C.byref(st)))
+    return st.as_dict()
+
+
 def rho_join_begin(R, nR: int, nS: int, *, key_shift: int = 0, stream: int | None = None,
                    algorithm: str = "RHO") -> None:
     """First half of a pipelined count join (mi355_rho_join_begin): plans both
@@ -514,6 +569,19 @@ def rho_join_tables(R, nR: int, S, nS: int, nthreads: int = 1, materialize: bool
     out = result_t()
     fn = lib.mi355_rht_join if algorithm == "RHT" else lib.mi355_rho_join
     _check(fn(C.byref(tR), C.byref(tS), C.byref(cfg), C.byref(out)))
+    return out
+
+
+def npo_join_tables(R, nR: int, S, nS: int, nthreads: int = 1, materialize: bool = False) -> result_t:
+    """The drop-in mi355_npo_join(table_t*, table_t*, joinconfig_t*, result_t*): the PHT
+    family's result_t, as rho_join_tables (chunked_table_triples / free_result)."""
+    tR = table_t(ptr(R), nR, 0, 0)
+    tS = table_t(ptr(S), nS, 0, 0)
+    cfg = joinconfig_t()
+    cfg.NTHREADS = nthreads
+    cfg.MATERIALIZE = 1 if materialize else 0
+    out = result_t()
+    _check(lib.mi355_npo_join(C.byref(tR), C.byref(tS), C.byref(cfg), C.byref(out)))
     return out
 
 
