@@ -18,6 +18,16 @@
 //       C++ symbol is exported for them: the reference's header declares NPO_st / NPO_no
 //       while its table names NPO_single_thread / NPO_no_overflow, so no consistent
 //       symbol exists to match.
+//   result_t *MWAY / PSM / RSM(const table_t*, const table_t*, const joinconfig_t*)
+//       mway/sortmergejoin_multiway.h:40-41, psm/parallel_sortmerge_join.h:16,
+//       radix/radix_sortmerge_join.hpp:4
+//       (_Z4MWAYPK7table_tS1_PK12joinconfig_t, _Z3PSMPK7table_tS1_PK12joinconfig_t,
+//        _Z3RSMPK7table_tS1_PK12joinconfig_t)
+//       All three run the one GPU sort-merge join (mi355_smj_join); relR->sorted / relS->sorted
+//       skip that relation's sort.  PSM prints the lines of its own print_timing
+//       (parallel_sortmerge_join.cpp:27-37), MWAY and RSM the 11-argument form
+//       (radix_join.cpp:199-215): the sorts under "Partition Overall", the merge under
+//       "Build+Join Overall", the pass, build and join in-depth values 0.
 // so an unmodified run_join-style caller (App/TEEBench/native.cpp:137, the TPC-H
 // queries) links against libsgxamd.so instead of the CPU join library.
 // With config->MATERIALIZE = 1 the result carries the reference's chunked_table_t
@@ -35,6 +45,9 @@ result_t *PHT(const table_t *relR, const table_t *relS, const joinconfig_t *conf
 result_t *PHT_no_overflow(const table_t *relR, const table_t *relS, const joinconfig_t *config);
 result_t *PHT_unrolled(const table_t *relR, const table_t *relS, const joinconfig_t *config);
 result_t *PHT_overflow(const table_t *relR, const table_t *relS, const joinconfig_t *config);
+result_t *MWAY(const table_t *relR, const table_t *relS, const joinconfig_t *config);
+result_t *PSM(const table_t *relR, const table_t *relS, const joinconfig_t *config);
+result_t *RSM(const table_t *relR, const table_t *relS, const joinconfig_t *config);
 
 void run_join(result_t *res, const table_t *relR, const table_t *relS, const char *algorithm_name,
               const joinconfig_t *config);

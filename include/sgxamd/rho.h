@@ -244,6 +244,65 @@ int mi355_npo_join_ex(const struct row_t *R, uint64_t nR, const struct row_t *S,
  * the radix fields 0. */
 int mi355_last_npo_stats(mi355_npo_stats *out);
 
+/*
+ * Sort-merge join: the reference's MWAY, PSM and RSM (mway/sortmergejoin_multiway.h,
+ * psm/parallel_sortmerge_join.h, radix/radix_sortmerge_join.hpp; table names at
+ * joins.cpp:44-47).  One GPU join stands behind the three names: R and S are sorted by key
+ * with a device-wide stable LSD radix sort (8-bit digits of key - the relation's smallest
+ * key; a pass whose digit is the same for every tuple of the relation is not run) and the two sorted relations are merge-joined.
+ * A counting join sorts the 4-byte keys only, a materialising join whole tuples.  The count
+ * is exact for any input.  Inputs are never modified, also when they are device-resident:
+ * the sort ping-pongs between workspace buffers.  No multi-GPU form (SGXAMD_GPUS is ignored
+ * for these names), no key_shift, no begin/finish pipeline.
+ */
+#define MI355_ALGO_SMJ 3 /* name only; mi355_rho_opts.algorithm does not accept it */
+
+typedef struct mi355_smj_opts {
+    int r_sorted, s_sorted;  /* 1 = that relation is already ascending by key: its sort is skipped
+                                (table_t.sorted; trusted, as the reference trusts it) and the
+                                merge reads it where it lies */
+    int materialize;         /* 1 = write every match to out, as mi355_rho_opts.materialize */
+    int timing;              /* 1 = record every launch (mi355_timing_get) */
+    void *stream;            /* hipStream_t to launch on; NULL = the library's stream */
+    struct output_triple_t *out; /* host or device memory; order unspecified */
+    uint64_t out_capacity;       /* triples that fit in out; if fewer than the matches, the call
+                                    returns MI355_ERR_CAPACITY with stats->matches = required
+                                    and writes nothing */
+} mi355_smj_opts;
+
+typedef struct mi355_smj_stats {
+    uint64_t matches;                      /* join cardinality */
+    uint32_t sort_passes_r, sort_passes_s; /* scatter passes actually run (0..4) */
+    uint32_t elem_bytes;                   /* 4: keys only (counting), 8: tuples (materialising) */
+    uint32_t sort_tile, merge_tile;        /* elements per workgroup tile in the sort / the merge */
+    uint32_t reserved0;
+    double ms_h2d;                         /* host->device staging (0 when inputs were resident) */
+    double ms_sort_r, ms_sort_s, ms_merge; /* 0 when timing is off: then only ms_total is measured */
+    double ms_total;                       /* both sorts + merge, device time */
+} mi355_smj_stats;
+
+/* Drop-in for MWAY(), PSM() and RSM(): same result contract as mi355_rho_join.  relR->sorted /
+ * relS->sorted become the opts' r_sorted / s_sorted. */
+int mi355_smj_join(const struct table_t *R, const struct table_t *S, const struct joinconfig_t *cfg,
+                   struct result_t *out);
+
+/* The join on raw tuple arrays (host or device, up to 2^31 tuples each).  nR == 0 or
+ * nS == 0: MI355_OK, 0 matches, no launch.  A null relation with a non-zero size:
+ * MI355_ERR_INVALID (checked before any device is touched).  Workspace that cannot be
+ * allocated: MI355_ERR_OOM.  Materialising counts first. */
+int mi355_smj_join_ex(const struct row_t *R, uint64_t nR, const struct row_t *S, uint64_t nS,
+                      const mi355_smj_opts *opts, mi355_smj_stats *stats);
+
+/* Statistics of the last sort-merge join on this thread.  mi355_last_join_stats reports
+ * its matches, ms_partition (= both sorts), ms_join (= merge) and ms_total, the radix fields 0. */
+int mi355_last_smj_stats(mi355_smj_stats *out);
+
+/* The sort on its own: out[0..n) = in[0..n) ascending by key, stable (equal keys keep input
+ * order).  in / out host or device memory, out != in; in is not modified.  passes (nullable)
+ * receives the scatter passes run: the bytes of key - smallest key that differ between
+ * tuples (0 when every key is equal: out is then a copy of in). */
+int mi355_sort_rows(const struct row_t *in, uint64_t n, struct row_t *out, uint32_t *passes, void *stream);
+
 /* HBM ceiling probe (measurement: bench.py's roofline ceilings).  One grid-stride
  * streaming kernel of 256-thread workgroups over device buffers, enqueued on `stream`
  * (null: the library stream): kind 0 copies `bytes` from src to dst, 1 reads src (dst:

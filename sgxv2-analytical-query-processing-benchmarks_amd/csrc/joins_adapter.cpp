@@ -5,6 +5,8 @@
 //      SGXv2Scripts/scripts/helpers/runner.py:14-55 parses our output unchanged.
 // PHT / PHT_no_overflow / PHT_unrolled / PHT_overflow: no_partitioning_hash_join.cpp:166-249 ->
 //      mi355_npo_join, plus the npj print_timing lines (HashLinkTableCommon.cpp:13-29).
+// MWAY / PSM / RSM: sortmergejoin_multiway.cpp, parallel_sortmerge_join.cpp,
+//      radix_sortmerge_join.cpp -> mi355_smj_join, plus their print_timing lines.
 // run_join: joins.cpp:55-78 (strcmp lookup in an algorithm table, memcpy of the
 //      result; like the reference, the callee's result_t is not freed).
 #include <algorithm>
@@ -67,6 +69,10 @@ const algorithm_t mi355_algorithms[] = {  // joins.cpp:33-53, the joins this lib
     {"PHT_o", PHT_overflow},
     {"NPO_st", npo_by_name},
     {"NPO_no", npo_by_name},
+    // the sort-merge family (joins.cpp:44-47): one GPU join behind every name
+    {"PSM", PSM},
+    {"RSM", RSM},
+    {"MWAY", MWAY},
     {"", nullptr},
 };
 
@@ -171,6 +177,65 @@ result_t *npo_by_name(const table_t *relR, const table_t *relS, const joinconfig
     return npo_dropin("NPO", relR, relS, config);
 }
 
+// MWAY, PSM and RSM: mi355_smj_join, then the reference's phase lines.  psm_form: the
+// lines of PSM's print_timing (parallel_sortmerge_join.cpp:27-37); otherwise the
+// 11-argument print_timing MWAY and RSM call (radix_join.cpp:199-215).  Both sorts are the
+// partition phase, the merge is the join phase; the in-depth values are 0.
+result_t *smj_dropin(const char *name, bool psm_form, const table_t *relR, const table_t *relS,
+                     const joinconfig_t *config) {
+    LOG_INFO("Running %s on MI355X (%s)", name, mi355_version());
+    const auto t_start = std::chrono::steady_clock::now();
+    auto *res = static_cast<result_t *>(std::malloc(sizeof(result_t)));
+    const int rc = mi355_smj_join(relR, relS, config, res);
+    const auto t_end = std::chrono::steady_clock::now();
+    if (rc != MI355_OK) {
+        LOG_ERROR("%s failed (%d): %s", name, rc, mi355_last_error());
+        std::exit(EXIT_FAILURE);
+    }
+    mi355_smj_stats st{};
+    mi355_last_smj_stats(&st);
+    const uint64_t num = relR->num_tuples + relS->num_tuples;
+    const double wall_us = std::chrono::duration<double, std::micro>(t_end - t_start).count();
+    const uint64_t C = cpms();
+    auto cyc = [&](double ms) { return static_cast<unsigned long>(ms * 1000.0 * C); };
+    const double n = num ? (double)num : 1.0;
+    const unsigned long total = cyc(st.ms_total), partition = cyc(st.ms_sort_r + st.ms_sort_s), join = cyc(st.ms_merge);
+    const unsigned long usec_tsc = total / C;
+    const double throughput = usec_tsc ? (double)num / (double)usec_tsc : 0.0;
+    LOG_INFO("Sort-merge join: %u + %u radix-sort passes over %u-byte elements (R sort %lu, S sort %lu cycles)",
+             st.sort_passes_r, st.sort_passes_s, st.elem_bytes, cyc(st.ms_sort_r), cyc(st.ms_sort_s));
+    LOG_INFO("Total input tuples : %u", (unsigned)num);
+    LOG_INFO("Result tuples : %lu", (unsigned long)st.matches);
+    LOG_INFO("Total Join Time (cycles)    : %lu", total);
+    LOG_INFO("Partition Overall (cycles)  : %lu", partition);
+    if (!psm_form) {
+        LOG_INFO("Partition Pass One (cycles) : %lu", 0ul);
+        LOG_INFO("Partition Pass Two (cycles) : %lu", 0ul);
+    }
+    LOG_INFO("Build+Join Overall (cycles) : %lu", join);
+    if (!psm_form) {
+        LOG_INFO("Build (cycles)              : %lu", 0ul);
+        LOG_INFO("Join (cycles)               : %lu", 0ul);
+    }
+    LOG_INFO("Cycles-per-tuple            : %.4lf", (double)total / n);
+    LOG_INFO("Cycles-per-tuple-partition  : %.4lf", (double)partition / n);
+    if (!psm_form) {
+        LOG_INFO("Cycles-per-tuple-partitioning_pass_1_timer     : %.4lf", 0.0);
+        LOG_INFO("Cycles-per-tuple-partitioning_pass_2_timer     : %.4lf", 0.0);
+    }
+    LOG_INFO("Cycles-per-tuple-join      : %.4lf", (double)join / n);
+    if (psm_form) {
+        LOG_INFO("Total Runtime (us) : %lu ", (unsigned long)wall_us);
+        LOG_INFO("Total RT from TSC (us) : %lu ", usec_tsc);
+        LOG_INFO("Throughput (M rec/sec) : %.2lf", throughput);
+    } else {
+        LOG_INFO("Pure Join Runtime (us) : %lu ", usec_tsc);
+        LOG_INFO("Throughput (M rec/sec) : %.2lf", throughput);
+        LOG_INFO("Total Runtime (us)     : %lu ", (unsigned long)wall_us);
+    }
+    return res;
+}
+
 }  // namespace
 
 result_t *PHT(const table_t *relR, const table_t *relS, const joinconfig_t *config) {
@@ -187,6 +252,18 @@ result_t *PHT_unrolled(const table_t *relR, const table_t *relS, const joinconfi
 
 result_t *PHT_overflow(const table_t *relR, const table_t *relS, const joinconfig_t *config) {
     return npo_dropin("PHT_overflow", relR, relS, config);
+}
+
+result_t *MWAY(const table_t *relR, const table_t *relS, const joinconfig_t *config) {
+    return smj_dropin("MWAY", false, relR, relS, config);
+}
+
+result_t *PSM(const table_t *relR, const table_t *relS, const joinconfig_t *config) {
+    return smj_dropin("PSM", true, relR, relS, config);
+}
+
+result_t *RSM(const table_t *relR, const table_t *relS, const joinconfig_t *config) {
+    return smj_dropin("RSM", false, relR, relS, config);
 }
 
 result_t *RHO(const table_t *relR, const table_t *relS, const joinconfig_t *config) {

@@ -85,9 +85,10 @@ void Timer::begin_call(hipStream_t s, bool enabled, bool coarse) {
 // -- R's pass-1 scatter and the build/probe -- and one "other" span between them, so a
 // timed step carries 4 events instead of one per kernel (each event between two kernels
 // costs 4.5-4.8 us of GPU time even without the system fence: r06q kernel trace).
-// The no-partitioning join's three spans (npo_*) are all kept.
+// The no-partitioning join's three spans (npo_*) and the sort-merge join's (smj_*) are all kept.
 static bool sparse_kept(const std::string &n) {
-    return n == "R_pass1_scatter" || n == "join_build_probe" || n.compare(0, 4, "npo_") == 0;
+    return n == "R_pass1_scatter" || n == "join_build_probe" || n.compare(0, 4, "npo_") == 0 ||
+           n.compare(0, 4, "smj_") == 0;
 }
 
 void Timer::mark(const char *name) {
@@ -196,7 +197,8 @@ void release_workspace(Context *ctx) {
                             &ctx->scratch.buf, &ctx->mat, &ctx->tp_mask, &ctx->tp_blk, &ctx->tp_trip, &ctx->scan_in,
                             &ctx->scan_out, &ctx->scan_aux, &ctx->scan_dict, &ctx->xsendR, &ctx->xsendS, &ctx->xrecvR,
                             &ctx->xrecvS, &ctx->wsendR, &ctx->wsendS, &ctx->wrecvR, &ctx->wrecvS, &ctx->wscratch.buf, &ctx->npo_table, &ctx->npo_bpay, &ctx->npo_nodes,
-                            &ctx->npo_npay})
+                            &ctx->npo_npay, &ctx->smj_ra, &ctx->smj_rb, &ctx->smj_sa, &ctx->smj_sb, &ctx->smj_ctrl,
+                            &ctx->smj_split})
         b->release();
     for (DeviceBuffer &b : ctx->tp_cols) b.release();
     for (DeviceBuffer &b : ctx->tp_rel) b.release();

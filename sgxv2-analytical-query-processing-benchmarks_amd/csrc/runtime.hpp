@@ -88,6 +88,9 @@ struct Context {
     // the overflow nodes and their payloads (the pool: allocated by the first join that
     // overflows a bucket)
     DeviceBuffer npo_table, npo_bpay, npo_nodes, npo_npay;
+    // sort-merge join (smj_host.cpp): the two ping-pong buffers of each relation's sort,
+    // the digit histograms + result words + per-tile counters, and the merge's chunk splits
+    DeviceBuffer smj_ra, smj_rb, smj_sa, smj_sb, smj_ctrl, smj_split;
     // TPC-H workspace: staged host columns, selection bits/offsets, intermediate
     // relations and join-result triples
     DeviceBuffer tp_cols[12], tp_mask, tp_blk, tp_rel[3], tp_trip;

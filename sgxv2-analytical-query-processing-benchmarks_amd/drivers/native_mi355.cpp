@@ -1,6 +1,8 @@
 // native_mi355 — the reference's native join driver (Join-Benchmarks/App/TEEBench/native.cpp)
-// running RHO, RHT or the PHT family (-a) on an MI355X through run_join() of libsgxamd.so; -m materialises
-// the result into the reference's chunked table (CHUNKED_TABLE build).
+// running RHO, RHT, the PHT family or the sort-merge family (MWAY, PSM, RSM) (-a) on an MI355X through
+// run_join() of libsgxamd.so; -m materialises the result into the reference's chunked table
+// (CHUNKED_TABLE build); --sort-r / --sort-s sort that relation by key after generation and mark it
+// sorted (generator.cpp:33-49), for every algorithm.
 //
 // Same CLI (commons.cpp:10-190 getopt "a:c:d:e:l:n:mr:s:t:u:x:y:z:hv"), the same
 // relation generation (seeds 11111 / 22222, pk R, fk / fk_sel / Zipf S: native.cpp:62-101,
@@ -23,7 +25,7 @@
 int main(int argc, char **argv) {
     uint64_t r_size = 2097152, s_size = 2097152;
     unsigned r_seed = 11111, s_seed = 22222;
-    int nthreads = 2, selectivity = 100, materialize = 0;
+    int nthreads = 2, selectivity = 100, materialize = 0, sort_r = 0, sort_s = 0;
     double skew = 0;
     char algorithm[128] = "RHO";
     static struct option long_options[] = {{"sort-r", no_argument, nullptr, 1},
@@ -33,6 +35,8 @@ int main(int argc, char **argv) {
     int c, idx = 0;
     while ((c = getopt_long(argc, argv, "a:c:d:e:l:n:mr:s:t:u:x:y:z:hv", long_options, &idx)) != -1) {
         switch (c) {
+            case 1: sort_r = 1; break;
+            case 2: sort_s = 1; break;
             case 'a': std::snprintf(algorithm, sizeof(algorithm), "%s", optarg); break;
             case 'd':
                 if (!std::strcmp(optarg, "cache-fit")) { r_size = 10ull * 1024 * 1024 / 8; s_size = 40ull * 1024 * 1024 / 8; }
@@ -47,7 +51,7 @@ int main(int argc, char **argv) {
             case 'x': r_size = std::strtoull(optarg, nullptr, 10) * 1024 * 1024 / 8; break;
             case 'y': s_size = std::strtoull(optarg, nullptr, 10) * 1024 * 1024 / 8; break;
             case 'z': skew = std::atof(optarg); break;
-            case 'h': std::printf("native_mi355 -a RHO|RHT|PHT|PHT_no|PHT_un|PHT_o|NPO_st|NPO_no -r N -s N [-l sel] [-z theta] [-n threads] [-m]\n"); return 0;
+            case 'h': std::printf("native_mi355 -a RHO|RHT|PHT|PHT_no|PHT_un|PHT_o|NPO_st|NPO_no|MWAY|PSM|RSM -r N -s N [-l sel] [-z theta] [-n threads] [-m] [--sort-r] [--sort-s]\n"); return 0;
             default: break;
         }
     }
@@ -69,6 +73,17 @@ int main(int argc, char **argv) {
         mi355_gen_fk(S.data(), s_size, (int64_t)r_size);
     }
     table_t tR{R.data(), r_size, 0, 0}, tS{S.data(), s_size, 0, 0};
+    // --sort-r / --sort-s: the relation ascending by key (stable), flagged as sorted
+    for (table_t *t : {sort_r ? &tR : nullptr, sort_s ? &tS : nullptr}) {
+        if (!t || t->num_tuples == 0) continue;
+        std::vector<row_t> sorted(t->num_tuples);
+        if (mi355_sort_rows(t->tuples, t->num_tuples, sorted.data(), nullptr, nullptr) != MI355_OK) {
+            std::printf("[ERROR] sorting the relation failed: %s\n", mi355_last_error());
+            return 1;
+        }
+        std::memcpy(t->tuples, sorted.data(), t->num_tuples * sizeof(row_t));
+        t->sorted = 1;
+    }
     joinconfig_t cfg{};
     cfg.NTHREADS = nthreads;
     cfg.MATERIALIZE = materialize;

@@ -154,6 +154,38 @@ class npo_stats(C.Structure):  # mi355_npo_stats
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+class smj_opts(C.Structure):  # mi355_smj_opts
+    _fields_ = [
+        ("r_sorted", C.c_int),
+        ("s_sorted", C.c_int),
+        ("materialize", C.c_int),
+        ("timing", C.c_int),
+        ("stream", C.c_void_p),
+        ("out", C.c_void_p),
+        ("out_capacity", C.c_uint64),
+    ]
+
+
+class smj_stats(C.Structure):  # mi355_smj_stats
+    _fields_ = [
+        ("matches", C.c_uint64),
+        ("sort_passes_r", C.c_uint32),
+        ("sort_passes_s", C.c_uint32),
+        ("elem_bytes", C.c_uint32),
+        ("sort_tile", C.c_uint32),
+        ("merge_tile", C.c_uint32),
+        ("reserved0", C.c_uint32),
+        ("ms_h2d", C.c_double),
+        ("ms_sort_r", C.c_double),
+        ("ms_sort_s", C.c_double),
+        ("ms_merge", C.c_double),
+        ("ms_total", C.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class multi_stats(C.Structure):  # sgxamd/multi.h
     _fields_ = [
         ("matches", C.c_uint64),
@@ -250,6 +282,10 @@ SIGNATURES = {
     "mi355_npo_join": (C.c_int, [C.POINTER(table_t), C.POINTER(table_t), C.POINTER(joinconfig_t), C.POINTER(result_t)]),
     "mi355_npo_join_ex": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, C.POINTER(npo_opts), C.POINTER(npo_stats)]),
     "mi355_last_npo_stats": (C.c_int, [C.POINTER(npo_stats)]),
+    "mi355_smj_join": (C.c_int, [C.POINTER(table_t), C.POINTER(table_t), C.POINTER(joinconfig_t), C.POINTER(result_t)]),
+    "mi355_smj_join_ex": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, C.POINTER(smj_opts), C.POINTER(smj_stats)]),
+    "mi355_last_smj_stats": (C.c_int, [C.POINTER(smj_stats)]),
+    "mi355_sort_rows": (C.c_int, [_P, C.c_uint64, _P, C.POINTER(C.c_uint32), _P]),
     # multi.h
     "mi355_rho_join_multi_ex": (C.c_int, [_P, C.c_uint64, _P, C.c_uint64, C.c_int, C.c_int, C.POINTER(rho_opts),
                                           C.POINTER(multi_stats)]),
@@ -454,6 +490,39 @@ def last_npo_stats() -> dict:
     return st.as_dict()
 
 
+def smj_join(R, nR: int, S, nS: int, *, r_sorted: bool = False, s_sorted: bool = False, timing: bool = False,
+             stream: int | None = None, materialize: bool = False, out=None, out_capacity: int = 0) -> JoinResult:
+    """Sort-merge join (the reference's MWAY / PSM / RSM) of nR R-tuples and nS S-tuples
+    (host or device): both relations are radix-sorted by key on the device, then merged.
+
+    r_sorted / s_sorted: that relation is already ascending by key, its sort is skipped.
+    `out` and out_capacity as rho_join (`out` implies materialize); stats is the dict of
+    mi355_smj_stats."""
+    mat = materialize or out is not None
+    o = smj_opts(1 if r_sorted else 0, 1 if s_sorted else 0, 1 if mat else 0, 1 if timing else 0, stream or None,
+                 ptr(out) if out is not None else None, out_capacity)
+    st = smj_stats()
+    rc = lib.mi355_smj_join_ex(ptr(R), nR, ptr(S), nS, C.byref(o), C.byref(st))
+    if rc == -5:
+        raise Mi355Error(rc, f"capacity: {int(st.matches)} triples needed")
+    _check(rc)
+    return JoinResult(int(st.matches), st)
+
+
+def last_smj_stats() -> dict:
+    st = smj_stats()
+    _check(lib.mi355_last_smj_stats(C.byref(st)))
+    return st.as_dict()
+
+
+def sort_rows(inp, n: int, out, stream: int | None = None) -> int:
+    """out[0..n) = inp[0..n) ascending by key, stable (mi355_sort_rows; host or device
+    buffers, out is not inp).  Returns the radix passes that ran."""
+    passes = C.c_uint32()
+    _check(lib.mi355_sort_rows(ptr(inp), n, ptr(out), C.byref(passes), stream or None))
+    return int(passes.value)
+
+
 def rho_join_begin(R, nR: int, nS: int, *, key_shift: int = 0, stream: int | None = None,
                    algorithm: str = "RHO") -> None:
     """First half of a pipelined count join (mi355_rho_join_begin): plans both
@@ -582,6 +651,21 @@ def npo_join_tables(R, nR: int, S, nS: int, nthreads: int = 1, materialize: bool
     cfg.MATERIALIZE = 1 if materialize else 0
     out = result_t()
     _check(lib.mi355_npo_join(C.byref(tR), C.byref(tS), C.byref(cfg), C.byref(out)))
+    return out
+
+
+def smj_join_tables(R, nR: int, S, nS: int, nthreads: int = 1, materialize: bool = False, r_sorted: bool = False,
+                    s_sorted: bool = False) -> result_t:
+    """The drop-in mi355_smj_join(table_t*, table_t*, joinconfig_t*, result_t*): the
+    sort-merge family's result_t, as rho_join_tables (chunked_table_triples / free_result);
+    r_sorted / s_sorted set table_t.sorted."""
+    tR = table_t(ptr(R), nR, 0, 1 if r_sorted else 0)
+    tS = table_t(ptr(S), nS, 0, 1 if s_sorted else 0)
+    cfg = joinconfig_t()
+    cfg.NTHREADS = nthreads
+    cfg.MATERIALIZE = 1 if materialize else 0
+    out = result_t()
+    _check(lib.mi355_smj_join(C.byref(tR), C.byref(tS), C.byref(cfg), C.byref(out)))
     return out
 
 
